@@ -6,12 +6,16 @@ RCCL gradient all-reduce when N>1, fused AdamW-amsgrad) over one batch of synthe
 two-domain sequences already resident in HBM.  Workload (N=1 line): Movie-Book item
 counts (36,845 + 63,937; BASELINE configs[2]), d=256, L=50, B=2048 per GPU, R=10,
 dropout 0.2, at the reference's precision (fp32 results: every product on split-bf16
-MFMAs with fp32 accumulation, parity 1e-4 vs the fp32 oracle).  Extra lines: the bf16
-performance mode on the same workload, BASELINE configs[1] (Food-Kitchen sizes, bf16)
-and configs[4] (C5 kernel roofline run).  Weak scaling: every rank trains its own batch
-of B, `value` = total sequences/s over all ranks.
+MFMAs with fp32 accumulation, parity 1e-4 vs the fp32 oracle).  Weak scaling: every rank
+trains its own batch of B, `value` = total sequences/s over all ranks.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints that one line.  With --full it
+also measures the extra lines (the bf16 performance mode on the same workload, BASELINE
+configs[1] (Food-Kitchen sizes, bf16), the C4 strong-scaling model and configs[4], the C5
+kernel roofline run; for N>1 the other exchange and propagation modes) and the CPU baseline
+of the oracle.  --dump-outputs DIR writes what the last timed step of the main line computed.
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
          N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -539,7 +543,7 @@ def run_c5(opt, world, rank, device, emit=True):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
@@ -547,14 +551,21 @@ def main():
     ap.add_argument('--config', default='mb', choices=list(CONFIGS) + ['c5'])
     ap.add_argument('--precision', default='fp32', choices=['bf16', 'fp32', 'fp32_exact'])
     ap.add_argument('--batch', type=int, default=0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the main line: the extra lines (other precision, other configurations, C4 model, C5 '
+                         'roofline run; N>1: the other exchange / propagation modes) and the CPU baseline of the oracle')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step of the main line computed as '
+                         'DIR/<name>.npy (float32): its three losses, and a fixed seeded sample of the parameters it '
+                         'left and of the gradient it accumulated')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--cpu-budget', type=float, default=20.0)
     ap.add_argument('--c5-seqs', type=int, default=2_000_000)
     ap.add_argument('--c5-tables', default='both', choices=['bf16', 'fp32', 'both'],
                     help='C5 [N, d] table storage (SURVEY.md §8(d): bf16 tables, the line\'s value; fp32 = the '
                          'product\'s autograd path; both: bf16 line + fp32_tables sub-object on the same graph)')
     ap.add_argument('--no-extra', dest='extra', action='store_false',
-                    help='skip the extra lines (MB bf16 mode, FK bf16, C5) of the default N=1 run')
+                    help='--full without the extra lines (MB bf16 mode, FK bf16, C4, C5; N>1: the other modes)')
     ap.add_argument('--no-c5', dest='c5_extra', action='store_false', help='skip the C5 extra line')
     ap.add_argument('--no-c4', dest='c4_extra', action='store_false', help='skip the C4 strong-scaling model line')
     ap.add_argument('--zero1', action='store_true',
@@ -565,8 +576,16 @@ def main():
     ap.add_argument('--dp-split', action='store_true',
                     help='strong scaling: every rank trains its slice of the same global batch (BASELINE '
                          'configs[3], e.g. --config ee --batch 4096)')
-    opt = ap.parse_args()
+    opt = ap.parse_args(argv)
+    if not opt.full:  # a plain run: the main line alone
+        opt.extra, opt.no_cpu_baseline = False, True
+    if opt.dump_outputs and opt.config == 'c5':
+        ap.error('--dump-outputs applies to the training configurations, not to the C5 kernel roofline run')
+    return opt
 
+
+def main():
+    opt = parse_args()
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     device = torch.device('cuda', 0)
@@ -592,7 +611,7 @@ def main():
     if opt.batch:
         cfg['B'] = opt.batch
     wl = workload(cfg, opt.config)
-    res = run_train(opt, cfg, opt.config, opt.precision, wl, world, rank, device)
+    res = run_train(opt, cfg, opt.config, opt.precision, wl, world, rank, device, dump=opt.dump_outputs)
     extra = {}
     if world > 1 and opt.extra:
         # the other exchange of the N>1 path: ZeRO-1 if the main line replicated AdamW,
@@ -715,8 +734,33 @@ def brief(r):
     return out
 
 
-def run_train(opt, cfg, name, precision, wl, world, rank, device, zero1=None, dp_split=None, gnn_shard=None):
-    """W untimed + K timed training steps of one configuration; returns the bench line (rank 0)."""
+DUMP_SAMPLE = 4_000_000  # elements kept of each sampled buffer (16 MB as float32)
+
+
+def dump_outputs(path, losses, flat):
+    """What a caller of the timed step holds after its last call, as <path>/<name>.npy (float32): the step's return
+    values loss, loss_rec, loss_mi ([1] each), and the state it updated — params, the flat parameter store after the
+    step's AdamW update, and grad, the gradient the steps accumulated into it (one device; under data parallelism the
+    accumulation is not kept whole).  A store larger than DUMP_SAMPLE elements is sampled at DUMP_SAMPLE positions
+    drawn once from a fixed seed (sorted; the same for both buffers and for every run)."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: v.detach().reshape(1) for k, v in zip(('loss', 'loss_rec', 'loss_mi'), losses)}
+    idx = None
+    if flat.numel > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(3407).integers(0, flat.numel, DUMP_SAMPLE))
+        idx = torch.from_numpy(idx).to(flat.param.device)
+    for k, buf in (('params', flat.param), ('grad', flat.accum if flat.direct else None)):
+        if buf is not None:
+            out[k] = buf if idx is None else buf[idx]
+    for k, v in out.items():
+        np.save(os.path.join(path, f'{k}.npy'), v.float().cpu().numpy())
+    log(f'[bench] outputs of the last timed step written to {path}: {", ".join(sorted(out))}')
+
+
+def run_train(opt, cfg, name, precision, wl, world, rank, device, zero1=None, dp_split=None, gnn_shard=None,
+              dump=None):
+    """W untimed + K timed training steps of one configuration; returns the bench line (rank 0).  ``dump``: a
+    directory for the outputs of the last timed step (dump_outputs; rank 0 writes)."""
     rows, gs, gp = wl
     B = cfg['B']
     n_rows = rows[0].shape[0]
@@ -785,6 +829,8 @@ def run_train(opt, cfg, name, precision, wl, world, rank, device, zero1=None, dp
     ms = el / opt.steps * 1e3
     value = B_global * opt.steps / el
     n_params = int(tr.model.flat.numel)
+    if dump and rank == 0:
+        dump_outputs(dump, last, tr.model.flat)
     del tr, batches
     peak = {'bf16': PEAK_BF16_TFLOPS, 'fp32': PEAK_X3_TFLOPS}.get(precision, PEAK_FP32_TFLOPS)
     roof = None

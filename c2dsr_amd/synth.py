@@ -35,12 +35,17 @@ def make_sequences(n_users: int, n_a: int, n_b: int, len_max: int, *, seed: int 
     perm_b = rng.permutation(n_b) + n_a
     n_min = max(2, min(n_min, len_max))
     lens = rng.integers(n_min, len_max + 1, size=n_users)
+    # rng.choice(n, size=k, p=p) is cdf.searchsorted(rng.random(k), side='right') on the normalised cumulative sum
+    # of p, which it rebuilds at every call; built once here, the draws (and the generator's stream) are the same
+    cdf_a, cdf_b = pa.cumsum(), pb.cumsum()
+    cdf_a /= cdf_a[-1]
+    cdf_b /= cdf_b[-1]
     seqs = []
     for n in lens:
         dom = rng.random(n) < p_a
         na, nb = int(dom.sum()), int(n - dom.sum())
-        ia = perm_a[rng.choice(n_a, size=na, p=pa)]
-        ib = perm_b[rng.choice(n_b, size=nb, p=pb)]
+        ia = perm_a[cdf_a.searchsorted(rng.random(na), side='right')]
+        ib = perm_b[cdf_b.searchsorted(rng.random(nb), side='right')]
         seq = np.empty(n, dtype=np.int64)
         seq[dom] = ia
         seq[~dom] = ib

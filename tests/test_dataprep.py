@@ -1,7 +1,6 @@
 """a1/a2 bit-exactness: index/mask construction and graph CSR vs the reference's
 own outputs (golden fixtures made by tools/gen_fixtures.py)."""
 import hashlib
-import os
 import random
 
 import numpy as np
@@ -54,14 +53,12 @@ def test_graph_csr_bit_exact(tmp_path, name):
         assert sorted(zip(ct.tolist(), rt.tolist(), vt.view(np.uint32).tolist())) == ref
 
 
-FK_RAW = '/root/reference/data/raw/Food-Kitchen/val_new.txt'
-
-
-@pytest.mark.skipif(not os.path.exists(FK_RAW), reason='Food-Kitchen raw file only in the build container')
-def test_food_kitchen_standin_bit_exact():
-    """The real FK val file processed as train/eval data and as the graph source."""
+def test_food_kitchen_standin_bit_exact(tmp_path):
+    """The real FK val file (tests/golden/fk_val_new.npz holds its bytes) processed as train/eval data and as the
+    graph source."""
     fk = G.load('fk_data.npz')
-    seqs = GR.read_sequences(FK_RAW)
+    (tmp_path / 'val_new.txt').write_bytes(G.load('fk_val_new.npz')['val_new_txt'].tobytes())
+    seqs = GR.read_sequences(str(tmp_path / 'val_new.txt'))
     n_a, n_b = 29207, 34886
     random.seed(3407)
     tr = np.asarray(DL.preprocess_train(seqs, n_a, n_b, 15), dtype=np.int64)

@@ -2,8 +2,8 @@
 
 main.py's loop (main.py:88-148: seeding, Trainer(args, noter), run_epoch, the StepLR step, run_test,
 cal_score) through the drop-in Trainer on the GPU, on the Food-Kitchen files the reference ships
-(tests/golden/fk_raw.npz: data/raw/Food-Kitchen/{val.txt, test_new.txt, items_a.txt, items_b.txt}; the
-train file is a missing blob, so train := val.txt, val := test := test_new.txt), at BASELINE configs[0]
+(tests/golden/fk_raw_{train,eval,items}.npz: data/raw/Food-Kitchen/{val.txt, test_new.txt, items_a.txt,
+items_b.txt}; the train file is a missing blob, so train := val.txt, val := test := test_new.txt), at BASELINE configs[0]
 (C1: d=64, L=15, B=128, R=10, 999 sampled negatives), dropout 0, fp32 mode — against the reference's own
 run of the same loop (tests/golden/traj_fk.npz, tools/gen_fixtures.py --fk-traj).
 
@@ -40,7 +40,7 @@ class Noter:
 
 
 def _raw_dir(tmp_path):
-    z = G.load('fk_raw.npz')
+    z = {k: v for part in ('train', 'eval', 'items') for k, v in G.load(f'fk_raw_{part}.npz').items()}
     raw = tmp_path / 'raw'
     raw.mkdir()
     for dst, src in (('train_new.txt', 'val_txt'), ('val_new.txt', 'test_new_txt'), ('test_new.txt', 'test_new_txt'),

@@ -15,8 +15,6 @@ from c2dsr_amd import graph as GR
 from c2dsr_amd import prep, synth
 from tests import goldens as G
 
-FK_RAW = '/root/reference/data/raw/Food-Kitchen/val_new.txt'
-
 
 def _raw(tmp_path, name='base'):
     d = G.load(f'data_{name}.npz')
@@ -94,12 +92,13 @@ def test_native_edges_match_python(tmp_path):
     np.testing.assert_array_equal(p1, p2)
 
 
-@pytest.mark.skipif(not os.path.exists(FK_RAW), reason='Food-Kitchen raw file only in the build container')
-def test_native_food_kitchen_checksums():
+def test_native_food_kitchen_checksums(tmp_path):
     """tests/golden/fk_data.npz: the reference's processing of the real FK val file (as train and as
-    eval data) and its graph; checked by sha256 like tests/test_dataprep.py."""
+    eval data) and its graph; checked by sha256 like tests/test_dataprep.py.  The file's bytes are
+    tests/golden/fk_val_new.npz."""
     fk = G.load('fk_data.npz')
-    rf = prep.RawFile(FK_RAW)
+    (tmp_path / 'val_new.txt').write_bytes(G.load('fk_val_new.npz')['val_new_txt'].tobytes())
+    rf = prep.RawFile(str(tmp_path / 'val_new.txt'))
     random.seed(3407)
     tr = rf.train_rows(29207, 34886, 15)
     arr = np.stack([tr[:, j] for j in range(14)], axis=1)

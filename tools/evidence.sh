@@ -2,27 +2,28 @@
 # Round evidence at the benched revision (every step under its own limit, chained):
 #   smoke, the default bench line, rocprofv3 kernel stats of the main line (+ idle gaps), FETCH / WRITE / SQ PMC passes
 #   of the main line, kernel stats + FETCH / WRITE passes of the C5 line (bf16 tables), the GPU suite.
-#   usage: bash tools/evidence.sh TAG        (outputs under gpurun_out/TAG_*)
+#   usage: bash tools/evidence.sh TAG        (outputs under $OUT/TAG_*)
 set -o pipefail
 TAG=${1:-r05z}
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-timeout -k 10 200 python -u -c 'import __graft_entry__ as g; g.smoke()' > gpurun_out/${TAG}_smoke.log 2>&1 || { tail -30 gpurun_out/${TAG}_smoke.log; exit 1; }
-tail -1 gpurun_out/${TAG}_smoke.log
-timeout -k 10 420 python3 bench.py > gpurun_out/${TAG}_bench.log 2>&1 || { tail -20 gpurun_out/${TAG}_bench.log; exit 1; }
-tail -1 gpurun_out/${TAG}_bench.log | cut -c1-300
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-extra > gpurun_out/${TAG}_prof.log 2>&1 || { tail -20 gpurun_out/${TAG}_prof.log; exit 1; }
-python tools/prof_summary.py gpurun_out/${TAG}_prof 13 45 > gpurun_out/${TAG}_summary.txt 2>&1
-python tools/gaps.py gpurun_out/${TAG}_prof > gpurun_out/${TAG}_gaps.txt 2>&1
+timeout -k 10 200 python -u -c 'import __graft_entry__ as g; g.smoke()' > $OUT/${TAG}_smoke.log 2>&1 || { tail -30 $OUT/${TAG}_smoke.log; exit 1; }
+tail -1 $OUT/${TAG}_smoke.log
+timeout -k 10 420 python3 bench.py --full > $OUT/${TAG}_bench.log 2>&1 || { tail -20 $OUT/${TAG}_bench.log; exit 1; }
+tail -1 $OUT/${TAG}_bench.log | cut -c1-300
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-extra > $OUT/${TAG}_prof.log 2>&1 || { tail -20 $OUT/${TAG}_prof.log; exit 1; }
+python tools/prof_summary.py $OUT/${TAG}_prof 13 45 > $OUT/${TAG}_summary.txt 2>&1
+python tools/gaps.py $OUT/${TAG}_prof > $OUT/${TAG}_gaps.txt 2>&1
 A="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra"
-timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/${TAG}_fetch -o run --output-format csv -- python3 $A > gpurun_out/${TAG}_fetch.log 2>&1 &&
-timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/${TAG}_write -o run --output-format csv -- python3 $A > gpurun_out/${TAG}_write.log 2>&1 &&
-timeout -s KILL 150 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_LDS SQ_BUSY_CYCLES -d gpurun_out/${TAG}_sq -o run --output-format csv -- python3 $A > gpurun_out/${TAG}_sq.log 2>&1 || { echo "pmc failed"; exit 1; }
+timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d $OUT/${TAG}_fetch -o run --output-format csv -- python3 $A > $OUT/${TAG}_fetch.log 2>&1 &&
+timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d $OUT/${TAG}_write -o run --output-format csv -- python3 $A > $OUT/${TAG}_write.log 2>&1 &&
+timeout -s KILL 150 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_LDS SQ_BUSY_CYCLES -d $OUT/${TAG}_sq -o run --output-format csv -- python3 $A > $OUT/${TAG}_sq.log 2>&1 || { echo "pmc failed"; exit 1; }
 C="bench.py --config c5 --c5-tables bf16 --steps 2 --warmup 1"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}c5_prof -o run --output-format csv -- python3 $C > gpurun_out/${TAG}c5_prof.log 2>&1 &&
-python tools/prof_summary.py gpurun_out/${TAG}c5_prof 3 20 > gpurun_out/${TAG}c5_summary.txt 2>&1 &&
-timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/${TAG}c5_fetch -o run --output-format csv -- python3 $C > gpurun_out/${TAG}c5_fetch.log 2>&1 &&
-timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/${TAG}c5_write -o run --output-format csv -- python3 $C > gpurun_out/${TAG}c5_write.log 2>&1 || { echo "c5 passes failed"; exit 1; }
-head -25 gpurun_out/${TAG}_summary.txt
-timeout -k 10 500 python -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread > gpurun_out/${TAG}_gputest.log 2>&1; echo "gputest rc=$?"
-tail -4 gpurun_out/${TAG}_gputest.log
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}c5_prof -o run --output-format csv -- python3 $C > $OUT/${TAG}c5_prof.log 2>&1 &&
+python tools/prof_summary.py $OUT/${TAG}c5_prof 3 20 > $OUT/${TAG}c5_summary.txt 2>&1 &&
+timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $OUT/${TAG}c5_fetch -o run --output-format csv -- python3 $C > $OUT/${TAG}c5_fetch.log 2>&1 &&
+timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -d $OUT/${TAG}c5_write -o run --output-format csv -- python3 $C > $OUT/${TAG}c5_write.log 2>&1 || { echo "c5 passes failed"; exit 1; }
+head -25 $OUT/${TAG}_summary.txt
+timeout -k 10 500 python -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread > $OUT/${TAG}_gputest.log 2>&1; echo "gputest rc=$?"
+tail -4 $OUT/${TAG}_gputest.log

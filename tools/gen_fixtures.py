@@ -12,6 +12,7 @@ copied.  Outputs are plain arrays (npz, no pickles) under tests/golden/:
   eval_<cfg>.npz   evaluate_batch ranks after the two steps (trainer.py:162-181)
   metrics.npz      cal_metrics / cal_score (utils/metrics.py)
   fk_data.npz      checksums + head of the Food-Kitchen val/test processing
+  fk_val_new.npz   the Food-Kitchen val_new.txt those checksums were made from, as bytes
   traj_<cfg>.npz   main.py's epoch loop driven through the reference Trainer(args, noter) for
                    N_EPOCH epochs (seeded like main.py:90-95, dropout 0, num_workers 0): per-epoch
                    train losses, the shuffled batch order, val/test ranks and cal_score
@@ -372,6 +373,9 @@ def gen_fk(ref):
         out[f'{k}_idx_sha256'] = np.frombuffer(hashlib.sha256(idx.tobytes()).digest(), dtype=np.uint8)
         out[f'{k}_val_sha256'] = np.frombuffer(hashlib.sha256(val.tobytes()).digest(), dtype=np.uint8)
     np.savez_compressed(os.path.join(OUT, 'fk_data.npz'), **out)
+    # the processed file itself, as bytes, for the tests that process it again
+    with open(os.path.join(a.path_raw, 'val_new.txt'), 'rb') as f:
+        np.savez_compressed(os.path.join(OUT, 'fk_val_new.npz'), val_new_txt=np.frombuffer(f.read(), dtype=np.uint8))
     print(f'[fk] trainlike={arr.shape} eval={len(ev)} nnz={out["share_nnz"]}/{out["specific_nnz"]}')
 
 
@@ -565,7 +569,8 @@ def gen_fk_trajectory(ref):
     data/raw/Food-Kitchen/val.txt and test_new.txt (train_new.txt is a missing blob), so
     train := val.txt and val := test := test_new.txt — at BASELINE configs[0] (C1: d=64, L=15 as main.py
     forces for FK, B=128, R=10, 999 sampled negatives), dropout 0, num_workers 0, FK_EPOCHS epochs.
-    Writes tests/golden/fk_raw.npz (the four raw input files as bytes) and traj_fk.npz: per-step losses,
+    Writes tests/golden/fk_raw_{train,eval,items}.npz (the four raw input files as bytes, in three files to keep
+    each small) and traj_fk.npz: per-step losses,
     per-epoch train losses, the shuffled batch order, val/test ranks, cal_metrics and cal_score."""
     ref_dl, ref_model, ref_trainer, ref_graph, ref_metrics = ref
     src = os.path.join(REF, 'data/raw/Food-Kitchen')
@@ -581,7 +586,9 @@ def gen_fk_trajectory(ref):
         data = open(os.path.join(src, f), 'rb').read()
         open(os.path.join(path_raw, dst), 'wb').write(data)
         raw[f] = np.frombuffer(data, dtype=np.uint8)
-    np.savez_compressed(os.path.join(OUT, 'fk_raw.npz'), **{k.replace('.', '_'): v for k, v in raw.items()})
+    raw = {k.replace('.', '_'): v for k, v in raw.items()}
+    for part, keys in (('train', ['val_txt']), ('eval', ['test_new_txt']), ('items', ['items_a_txt', 'items_b_txt'])):
+        np.savez_compressed(os.path.join(OUT, f'fk_raw_{part}.npz'), **{k: raw[k] for k in keys})
     cfg = dict(n_a=29207, n_b=34886, len_max=15, len_rec=10, d_latent=64, n_gnn=1, n_attn=1, n_head=1,
                norm_first=False, d_bias=False, shared_item_embed=False)
     args = make_args(cfg, path_raw, path_data)
