@@ -1606,3 +1606,133 @@ def rank_metrics(rank, xory, dom, sums):
     xory = xory.reshape(-1).contiguous().long()
     lib('c2dsr_rank_metrics', rank, xory, rank.numel(), int(dom), sums, stream())
     return sums
+
+
+# ----------------------------------------------------------------------------- full-catalogue top-K / full ranking
+TOPK_MAX_K = 128  # csrc/topk.hip: the candidate lists hold up to 2 · 128 keys
+TOPK_MAX_D = 256  # the widest instantiated image (64 / 128 / 256; a narrower d is zero-padded, exactly)
+_TOPK_IMG = {}  # (W data_ptr, shape, D) -> ((WEIGHTS.epoch, W._version), split image of W padded to width D, W)
+
+
+def _topk_width(d):
+    if d < 1 or d > TOPK_MAX_D:
+        raise ValueError(f'full_topk: d = {d} outside 1..{TOPK_MAX_D}')
+    return 64 if d <= 64 else 128 if d <= 128 else 256
+
+
+def _split_image_padded(X, D):
+    """[rows][2D] hi ‖ lo image of fp32 X [rows][d], columns d..D zero."""
+    rows, d = X.shape
+    out = torch.empty(rows, 2 * D, device=X.device, dtype=torch.bfloat16)
+    lib('c2dsr_f32_split_bf16_pad', X, rows, d, D, rows, out, stream())
+    return out
+
+
+def _topk_weight_image(W, D):
+    key = (W.data_ptr(), tuple(W.shape), D)
+    tag = (WEIGHTS.epoch, W._version)
+    hit = _TOPK_IMG.get(key)
+    if hit is not None and hit[0] == tag:
+        return hit[1]
+    if len(_TOPK_IMG) >= 8:
+        _TOPK_IMG.clear()
+    img = _split_image_padded(W, D)
+    _TOPK_IMG[key] = (tag, img, W)  # W kept alive: its address cannot be handed to another tensor while cached
+    return img
+
+
+def eval_query(h_share, h_a, h_b, idx_last_a, idx_last_b, xory, seq_a=None, seq_b=None, n_item_a=0):
+    """The evaluation rows' queries, as eval_rank builds them: q[i] = h_share[i, -1] + h_dom[i, idx_last_dom[i]]
+    (csrc/topk.hip).  Returns (q fp32 [B, d], bad int32 [B] — 1 where idx_last is out of range —, seen): with
+    seq_a / seq_b given, seen int64 [B, L] holds each row's own sequence as domain-local item ids (padding and the
+    other domain's ids fall outside the domain's range), else None."""
+    require_device(h_share)
+    B, L, d = h_share.shape
+    for t in (h_a, h_b):
+        if t.shape != h_share.shape:
+            raise ValueError('h_share / hx / hy shapes differ')
+    ints = [x.reshape(-1).contiguous().long() for x in (idx_last_a, idx_last_b, xory)]
+    for x in ints:
+        if x.numel() != B:
+            raise ValueError('idx_last / xory must hold one entry per row')
+    if (seq_a is None) != (seq_b is None):
+        raise ValueError('seq_a and seq_b go together')
+    seen = None
+    if seq_a is not None:
+        seq_a, seq_b = seq_a.contiguous().long(), seq_b.contiguous().long()
+        if tuple(seq_a.shape) != (B, L) or tuple(seq_b.shape) != (B, L):
+            raise ValueError('seq_a / seq_b must be [B, L]')
+        seen = torch.empty(B, L, dtype=torch.int64, device=h_share.device)
+    q = torch.empty(B, d, dtype=torch.float32, device=h_share.device)
+    bad = torch.empty(B, dtype=torch.int32, device=h_share.device)
+    lib('c2dsr_eval_query', h_share.contiguous(), h_a.contiguous(), h_b.contiguous(), B, L, d, *ints, seq_a, seq_b,
+        int(n_item_a), q, bad, seen, stream())
+    return q, bad, seen
+
+
+def full_topk(q, W, b, k, *, target=None, exclude=None, dom=None, which=0, n_split=None, out=None, bad=None):
+    """The k best items of one classifier head for every query row, and (with ``target``) the target's rank among
+    ALL items: s(i, j) = q[i] · W[j] + b[j] swept over the whole catalogue at split-bf16 ×3 precision, never
+    materialised (csrc/topk.hip).  Returns (ids int64 [M, k], scores fp32 [M, k], rank int32 [M] or None) on the
+    device: score descending, id ascending among equal scores; rank = 1 + #{j : s(i, j) > s(i, target_i)}.
+
+    exclude int64 [M, E]: ids that must not appear in the row's top-k (entries outside [0, n) are ignored; rank is
+    not affected; a tail that cannot be filled is (-1, -inf)).  dom int64 [M] / which: only rows with
+    (dom != 0) == (which != 0) are computed and written.  out = (ids, scores, rank): buffers to write into (two heads
+    over one mixed batch).  bad int32 [M]: flagged rows get ids -1 and rank -1.  n_split: workgroup columns per row
+    block (default: about one workgroup per CU); the results do not depend on it."""
+    if q.dim() != 2 or W.dim() != 2 or b.dim() != 1:
+        raise ValueError('full_topk: q [M, d], W [n, d], b [n]')
+    M, d = q.shape
+    n = W.shape[0]
+    k = int(k)
+    if k < 1 or k > TOPK_MAX_K:
+        raise ValueError(f'full_topk: k = {k} outside 1..{TOPK_MAX_K}')
+    if k > n:
+        raise ValueError(f'full_topk: k = {k} exceeds the {n} items')
+    if W.shape[1] != d or b.shape[0] != n:
+        raise ValueError('full_topk: q / W / b shapes do not match')
+    D = _topk_width(d)
+    if which not in (0, 1):
+        raise ValueError('full_topk: which must be 0 or 1')
+    if n_split is not None and int(n_split) < 1:
+        raise ValueError('full_topk: n_split must be at least 1')
+    for name, t in (('target', target), ('dom', dom), ('bad', bad)):
+        if t is not None and t.numel() != M:
+            raise ValueError(f'full_topk: {name} must hold one entry per row')
+    E = 0
+    if exclude is not None:
+        if exclude.dim() != 2 or exclude.shape[0] != M:
+            raise ValueError('full_topk: exclude must be [M, E]')
+        E = exclude.shape[1]
+    if out is not None:
+        ids, scores, rank = out
+        if (tuple(ids.shape) != (M, k) or ids.dtype != torch.int64 or tuple(scores.shape) != (M, k)
+                or scores.dtype != torch.float32 or not ids.is_contiguous() or not scores.is_contiguous()):
+            raise ValueError('full_topk: out ids int64 [M, k] / scores fp32 [M, k], contiguous')
+        if target is not None and (rank is None or tuple(rank.shape) != (M,) or rank.dtype != torch.int32):
+            raise ValueError('full_topk: out rank int32 [M]')
+    for t in (q, W, b, target, exclude, dom, bad) + (tuple(out) if out is not None else ()):
+        if t is not None:
+            require_device(t)
+    dev = q.device
+    if out is None:
+        ids = torch.empty(M, k, dtype=torch.int64, device=dev)
+        scores = torch.empty(M, k, dtype=torch.float32, device=dev)
+        rank = torch.empty(M, dtype=torch.int32, device=dev) if target is not None else None
+    if target is None:
+        rank = None
+    if M == 0:
+        return ids, scores, rank
+    ns = int(n_split) if n_split is not None else int(lib.raw('c2dsr_full_topk_splits')(M, n))
+    ws_bytes = int(lib.raw('c2dsr_full_topk_workspace')(M, n, k, ns))
+    if ws_bytes <= 0:
+        raise ValueError('full_topk: shape not supported')
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    Qx = _split_image_padded(q.detach().contiguous().float(), D)
+    Wx = _topk_weight_image(W.detach().contiguous(), D)
+    i64 = lambda t: None if t is None else t.reshape(-1).contiguous().long()  # noqa: E731
+    lib('c2dsr_full_topk', Qx, Wx, b.detach().contiguous(), M, n, D, k, ns, i64(target),
+        None if E == 0 else exclude.contiguous().long(), E, i64(dom), int(which),
+        None if bad is None else bad.reshape(-1).contiguous().int(), ids, scores, rank, ws, ws_bytes, stream())
+    return ids, scores, rank

@@ -583,3 +583,56 @@ class Trainer(object):
                 rank, flag = self.eval_ranks(batch)
                 acc.add(rank, flag)
         return acc
+
+    # ------------------------------------------------------------------ full-catalogue ranking / recommendation
+    def _full_heads(self, batch, k, target, exclude_seen):
+        """Both heads' full-catalogue sweeps (csrc/topk.hip) over one mixed batch into shared outputs: head a
+        writes the rows with xory == 0, head b the others — no host read, no row permutation."""
+        seq_share, seq_a, seq_b, pos, pos_a, pos_b, idx_last_a, idx_last_b, xory_last = [
+            x.to(self.device) for x in batch[:9]]
+        h_share, hx, hy = self.model(seq_share, seq_a, seq_b, pos, pos_a, pos_b)
+        m = self.model
+        xory = xory_last.reshape(-1).contiguous().long()
+        q, bad, seen = ops.eval_query(h_share, hx, hy, idx_last_a, idx_last_b, xory,
+                                      seq_a if exclude_seen else None, seq_b if exclude_seen else None,
+                                      self.n_item_a)
+        B = q.shape[0]
+        out = (torch.empty(B, k, dtype=torch.int64, device=self.device),
+               torch.empty(B, k, dtype=torch.float32, device=self.device),
+               torch.empty(B, dtype=torch.int32, device=self.device) if target is not None else None)
+        for which, head in ((0, m.classifier_a), (1, m.classifier_b)):
+            ops.full_topk(q, head.weight, head.bias, k, target=target, exclude=seen, dom=xory, which=which, out=out,
+                          bad=bad)
+        return out, bad, xory
+
+    def full_ranks(self, batch):
+        """Device ranks of one evaluation batch under the full-ranking protocol: the held-out item against the
+        WHOLE catalogue of its domain (rank = 1 + #{j : s(j) > s(gt)}, ties not counted), instead of eval_ranks'
+        sampled negatives (``list_neg`` is ignored).  Same contract as eval_ranks: (rank int32 [B], xory int64 [B]),
+        rank -1 for an index out of range.  The model is in eval() with convolve_graph() done by the caller."""
+        gt = batch[9].to(self.device).reshape(-1)
+        (_, _, rank), _, xory = self._full_heads(batch, 1, gt, False)
+        return rank, xory
+
+    def evaluate_full(self, loader):
+        """Metrics of a whole evaluation pass under the full-ranking protocol (one host sync, at ``.values()``):
+        returns a metrics.RankMetrics like evaluate_metrics."""
+        acc = RankMetrics(self.device)
+        self.model.eval()
+        with torch.no_grad():
+            self.model.convolve_graph()
+            for batch in loader:
+                rank, flag = self.full_ranks(batch)
+                acc.add(rank, flag)
+        return acc
+
+    def recommend(self, batch, k=20, exclude_seen=True):
+        """The k best items for every row of ``batch`` (the first nine evaluation fields), in the domain
+        ``xory_last`` names for the row: (ids int64 [B, k], scores fp32 [B, k]) on the device, ids domain-local as
+        ``gt_last`` is, best first.  exclude_seen drops the row's own in-domain history; a tail that cannot be filled
+        is (-1, -inf).  One small host read per call: IndexError on an ``idx_last`` out of range."""
+        with torch.no_grad():
+            (ids, scores, _), bad, _ = self._full_heads(batch, int(k), None, bool(exclude_seen))
+        if bool(bad.any()):
+            raise IndexError('evaluation index out of range (idx_last)')
+        return ids, scores

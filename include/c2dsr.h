@@ -531,6 +531,46 @@ int c2dsr_eval_rank(const float* h_share, const float* h_a, const float* h_b, in
  * are sums[k]/count; accumulating over all batches of an evaluation costs one host sync per epoch. */
 int c2dsr_rank_metrics(const int* rank, const int64_t* xory, int B, int dom, double* sums, void* stream);
 
+/* Full-catalogue top-K and full ranking (csrc/topk.hip): what the sampled protocol above does not give — the k best
+ * items of a head for a query, and the target's rank among ALL n items.  Scores s(i, j) = q_i · W_j + b_j over
+ * every j in [0, n) are swept once at split-bf16 x3 precision (hi·hi + lo·hi + hi·lo, fp32 accumulate, whatever the
+ * model's precision mode) and never stored as an [M][n] array.
+ * c2dsr_full_topk_supported: 1 for the instantiated image widths D (64, 128, 256); a narrower d is served by
+ * zero-padded images (c2dsr_f32_split_bf16_pad; padding is exact). */
+int c2dsr_full_topk_supported(int d);
+/* the default number of column splits for M query rows over n items (about one workgroup per CU) */
+int c2dsr_full_topk_splits(int M, int n);
+/* workspace bytes of c2dsr_full_topk: per (row, split) a candidate list of 2·KP keys (KP = k rounded up to 32, 64
+ * or 128) and two counts — O(M·k·n_split), independent of n; 0 for arguments c2dsr_full_topk would refuse */
+size_t c2dsr_full_topk_workspace(int M, int n, int k, int n_split);
+/* c2dsr_f32_split_bf16 with the d columns of x [rows][d] zero-padded to D >= d: out [rows_out][2·D] = hi ‖ lo, zero
+ * rows from `rows` up to rows_out (any d >= 1) */
+int c2dsr_f32_split_bf16_pad(const float* x, long rows, int d, int D, long rows_out, void* out, void* stream);
+/* The query of evaluation row i, as the head of c2dsr_eval_rank builds it: q[i] = h_share[i, L-1] +
+ * h_dom[i, idx_last_dom[i]] (dom = a iff xory[i] == 0; the same fp32 add; a negative idx_last wraps once).  q fp32
+ * [B][d]; bad int32 [B]: 1 where idx_last is outside [-L, L) (q[i] = 0; c2dsr_full_topk then gives the row rank -1
+ * and ids -1).  seen (optional, with seq_a / seq_b int64 [B][L]): the row's own sequence as domain-local item ids
+ * int64 [B][L] — seq_a for a-rows, seq_b - n_item_a for b-rows; padding and other-domain ids fall outside [0, n). */
+int c2dsr_eval_query(const float* h_share, const float* h_a, const float* h_b, int B, int L, int d,
+                     const int64_t* idx_last_a, const int64_t* idx_last_b, const int64_t* xory,
+                     const int64_t* seq_a, const int64_t* seq_b, int64_t n_item_a, float* q, int* bad, int64_t* seen,
+                     void* stream);
+/* Per query row i (Qx: split image [M][2·D] of q; Wx: split image of W, at least n rows; bias fp32 [n]):
+ *   ids / scores [M][k]: the k items with the largest scores, score descending, then id ascending among bit-equal
+ *     scores (int64 / fp32); 1 <= k <= 128, k <= n.  exclude (optional) int64 [M][E]: ids that must not appear for
+ *     the row (entries outside [0, n) are ignored); when fewer than k remain the tail is (-1, -inf).
+ *   rank [M] (optional, needs target int64 [M]): 1 + #{j in [0, n) : s(i, j) > s(i, target_i)} — strict, over the
+ *     whole catalogue whatever `exclude` holds; the target's score comes out of the same instruction sequence as
+ *     every swept column.  A negative target wraps once (as c2dsr_eval_rank); outside [-n, n): rank -1.
+ *   dom (optional) int64 [M] with which in {0, 1}: only rows with (dom[i] != 0) == (which != 0) are computed and
+ *     written, the others' outputs are left untouched (two heads over one mixed batch into shared outputs).
+ *   bad (optional) int32 [M]: a nonzero row gets ids -1, scores -inf, rank -1.
+ * n_split >= 1 workgroup columns per 128-row block; the results are bitwise independent of n_split and of
+ * scheduling.  ws: c2dsr_full_topk_workspace(M, n, k, n_split) bytes. */
+int c2dsr_full_topk(const void* Qx, const void* Wx, const float* bias, int M, int n, int D, int k, int n_split,
+                    const int64_t* target, const int64_t* exclude, int E, const int64_t* dom, int which,
+                    const int* bad, int64_t* ids, float* scores, int* rank, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
