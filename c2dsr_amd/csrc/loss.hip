@@ -76,8 +76,12 @@ __global__ __launch_bounds__(256) void pool2_fwd_kernel(const float* __restrict_
         x1[u] = l < L ? wa[l] : 0.f;
         x2[u] = (wb && l < L) ? wb[l] : 0.f;
         const long bl = (long)b * L + l;
-        v[u] = (cin && (x1[u] != 0.f || x2[u] != 0.f)) ? *(const float4*)(h + (hmap ? hmap[bl] : bl) * d + c)
-                                                        : c2::f4(0.f);
+        // a NaN weight (a sequence whose mask is empty: 0 / 0, as cal_mask) is != 0 too, and its rows are in no
+        // row subset: a row mapped to -1 is not read and contributes a zero vector (the NaN weight still makes
+        // that sequence's output NaN)
+        long hr = -1;
+        if (cin && (x1[u] != 0.f || x2[u] != 0.f)) hr = hmap ? hmap[bl] : bl;
+        v[u] = hr >= 0 ? *(const float4*)(h + hr * d + c) : c2::f4(0.f);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -108,9 +112,13 @@ __global__ void pool2_bwd_kernel(const float* __restrict__ d1, const float* __re
   const int c = (int)(e % d);
   const long k = e / d;
   const long bl = idx ? idx[k] : k;
+  float4 o = accumulate ? *(const float4*)(dh + e) : c2::f4(0.f);
+  if (bl < 0) {  // a compact row mapped to no (b, l) (-1): no weight is read, the row receives a zero vector
+    *(float4*)(dh + e) = o;
+    return;
+  }
   const long b = bl / L;
   const float x1 = w1[bl], x2 = d2 ? w2[bl] : 0.f;
-  float4 o = accumulate ? *(const float4*)(dh + e) : c2::f4(0.f);
   if (x1 != 0.f) o = c2::fma4(x1, *(const float4*)(d1 + b * d + c), o);
   if (x2 != 0.f) o = c2::fma4(x2, *(const float4*)(d2 + b * d + c), o);
   *(float4*)(dh + e) = o;

@@ -205,8 +205,10 @@ int c2dsr_pool_bwd(const float* dout, const float* w, int B, int L, int d, float
  * out2[b] = Σ_l h[b,l]·w2[b,l] (w2 may be null); and the backward in write or accumulate mode:
  * dh[b,l] = (accumulate ? dh[b,l] : 0) + d1[b]·w1[b,l] + d2[b]·w2[b,l] (d2 may be null).
  * Row subsets (an encoder pass whose last layer ran on the rows the loss reads): h row (b,l) is
- * h[hmap[b·L+l]] (hmap null: identity; every row with a nonzero weight must be mapped); the backward
- * writes the n_rows rows of a compact dh, row k being (b,l) = idx[k] (idx null: all B·L rows). */
+ * h[hmap[b·L+l]] (hmap null: identity; every row with a nonzero weight must be mapped — a row mapped to -1 is
+ * not read and counts as a zero vector: the rows of a sequence with an empty mask, whose weights are NaN (0 / 0),
+ * are in no subset, and its outputs are NaN as the reference's); the backward writes the n_rows rows of a compact
+ * dh, row k being (b,l) = idx[k] (idx null: all B·L rows; idx[k] = -1: no weight read, the row gets a zero vector). */
 int c2dsr_pool2_fwd(const float* h, const int* hmap, const float* w1, const float* w2, int B, int L, int d,
                     float* out1, float* out2, void* stream);
 int c2dsr_pool2_bwd(const float* d1, const float* w1, const float* d2, const float* w2, int B, int L, int d,

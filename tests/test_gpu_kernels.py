@@ -261,32 +261,152 @@ def test_attention_short_batch_at_allocation_end(B, L, d, H, p):
     _attention_case(B, L, d, H, p, tail=True)
 
 
-@pytest.mark.parametrize('d', [16, 64, 256, 512])
-@pytest.mark.parametrize('p', [0.0, 0.2])
-def test_add_layernorm_fwd_bwd(d, p):
+def _add_layernorm_case(rows, d, p, mapped=False, ref_dtype=torch.float32):
+    """AddLNFn (c2dsr_add_ln_fwd / c2dsr_ln_bwd) against the same formula in torch on the CPU, in ``ref_dtype``
+    from the same fp32 inputs; mapped: the dropout rows come from a row map (a row subset of a 4x larger layout)."""
     from c2dsr_amd import ops
     from oracle.c2dsr_oracle import keep_mask
-    rows = 777
-    a, b = torch.randn(rows, d), torch.randn(rows, d)
-    w, bias = torch.randn(d), torch.randn(d)
+    g = torch.Generator().manual_seed(rows * 7 + d)
+    a, b = torch.randn(rows, d, generator=g), torch.randn(rows, d, generator=g)
+    w, bias = torch.randn(d, generator=g), torch.randn(d, generator=g)
     keys = (5, 6)
+    rmap = torch.sort(torch.randperm(4 * rows, generator=g)[:rows])[0] if mapped else torch.arange(rows)
     ad, bd = a.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
     wd = w.to(DEV).requires_grad_(True)
     bsd = bias.to(DEV).requires_grad_(True)
-    y = ops.AddLNFn.apply(ad, bd, wd, bsd, p, keys, 10, 1e-8)
-    idx = (np.arange(rows)[:, None] + 10) * d + np.arange(d)[None, :]
-    mk = torch.from_numpy(keep_mask(idx, keys, p).astype(np.float32)) / (1 - p)
-    ar, br, wr, bbr = [t.clone().requires_grad_(True) for t in (a, b, w, bias)]
+    y = ops.AddLNFn.apply(ad, bd, wd, bsd, p, keys, 10, 1e-8, None, rmap.to(torch.int32).to(DEV) if mapped else None)
+    idx = (rmap.numpy()[:, None] + 10) * d + np.arange(d)[None, :]
+    mk = (torch.from_numpy(keep_mask(idx, keys, p).astype(np.float32)) / (1 - p)).to(ref_dtype)
+    ar, br, wr, bbr = [t.clone().to(ref_dtype).requires_grad_(True) for t in (a, b, w, bias)]
     x = ar + br * mk
     mu = x.mean(-1, keepdim=True)
     var = ((x - mu) ** 2).mean(-1, keepdim=True)
     ref = (x - mu) / torch.sqrt(var + 1e-8) * wr + bbr
     assert rel(y, ref) < 1e-5
-    gy = torch.randn(rows, d)
+    gy = torch.randn(rows, d, generator=g)
     y.backward(gy.to(DEV))
-    ref.backward(gy)
+    ref.backward(gy.to(ref_dtype))
     for got, want in ((ad.grad, ar.grad), (bd.grad, br.grad), (wd.grad, wr.grad), (bsd.grad, bbr.grad)):
         assert rel(got, want) < 2e-5
+
+
+# d = 768 / 1024: three / four float4 per lane; 4, 12: fewer columns than the narrowest lane group covers; 100, 320:
+# no power of two (lpr_for(100) = 32 with 7 masked lanes); these against float64
+@pytest.mark.parametrize('d', [16, 64, 256, 512, 4, 12, 100, 320, 768, 1024])
+@pytest.mark.parametrize('p', [0.0, 0.2])
+def test_add_layernorm_fwd_bwd(d, p):
+    _add_layernorm_case(777, d, p, ref_dtype=torch.float32 if d in (16, 64, 256, 512) else torch.float64)
+
+
+# more rows than the backward's capped grid covers in one step (1024 blocks x 256 / LPR rows, two rows per step),
+# with an uneven remainder, and a mapped (row-subset) case; against float64
+@pytest.mark.parametrize('rows,d,p,mapped', [(9001, 256, 0.2, False), (70001, 16, 0.2, False), (777, 64, 0.2, True),
+                                             (9001, 256, 0.1, True)])
+def test_add_layernorm_rows_past_grid_cap(rows, d, p, mapped):
+    _add_layernorm_case(rows, d, p, mapped, torch.float64)
+
+
+def test_layernorm_refuses_d_over_1024():
+    from c2dsr_amd._lib import HipLibError, lib, stream
+    rows, d = 8, 1028
+    t = lambda *sh: torch.zeros(*sh, device=DEV)  # noqa: E731
+    with pytest.raises(HipLibError, match='hipError 1'):
+        lib('c2dsr_add_ln_fwd', t(rows, d), None, rows, d, 0, 0, 0.0, 0, None, t(d), t(d), 1e-8, None, t(rows, d),
+            t(rows), t(rows), stream())
+    ws = torch.empty(lib.raw('c2dsr_ln_bwd_workspace')(d), dtype=torch.uint8, device=DEV)
+    with pytest.raises(HipLibError, match='hipError 1'):
+        lib('c2dsr_ln_bwd', t(rows, d), t(rows), t(rows), t(d), t(rows, d), rows, d, t(rows, d), 0, None, 0, 0, 0.0, 0,
+            None, t(d), t(d), ws, stream())
+
+
+@pytest.mark.parametrize('rows2,rows1,d', [(777, 300, 256), (5000, 4099, 256), (64, 0, 512), (0, 50, 64)])
+def test_ln_reduce2_equals_own_reductions(rows2, rows1, d):
+    """c2dsr_ln_reduce2 (the parameter gradients of c2dsr_ln2_bwd and c2dsr_ln_bwd, run with null gradient outputs,
+    in one launch) adds the same bits onto prefilled gradients as the two backwards' own reductions."""
+    from c2dsr_amd._lib import lib, stream
+    g = torch.Generator().manual_seed(rows2 + rows1 + d)
+    t = lambda *sh: torch.randn(*sh, generator=g).to(DEV)  # noqa: E731
+    s = stream()
+    w2, b2, wF, bF, w1, b1 = t(d) * 0.5 + 1, t(d) * 0.1, t(d) * 0.5 + 1, t(d) * 0.1, t(d) * 0.5 + 1, t(d) * 0.1
+    keys, base, p = (7, 9), 11, 0.2
+    ws2 = torch.empty(lib.raw('c2dsr_ln2_bwd_workspace')(d), dtype=torch.uint8, device=DEV)
+    ws1 = torch.empty(lib.raw('c2dsr_ln_bwd_workspace')(d), dtype=torch.uint8, device=DEV)
+    pre = [t(d) for _ in range(6)]  # nonzero gradients already there
+    if rows2:
+        a, b, dy2 = t(rows2, d), t(rows2, d), t(rows2, d)
+        xs, y2, st = torch.empty_like(a), torch.empty_like(a), torch.empty(4, rows2, device=DEV)
+        lib('c2dsr_add_ln2_fwd', a, b, rows2, d, keys[0], keys[1], p, base, None, w2, b2, 1e-8, wF, bF, 1e-8, xs, y2,
+            st, s)
+    if rows1:
+        x1, dy1 = t(rows1, d), t(rows1, d)
+        y1, m1, r1 = torch.empty_like(x1), torch.empty(rows1, device=DEV), torch.empty(rows1, device=DEV)
+        lib('c2dsr_add_ln_fwd', x1, None, rows1, d, 0, 0, 0.0, 0, None, w1, b1, 1e-8, None, y1, m1, r1, s)
+
+    def backwards(gr):  # gr: six gradient outputs or six None
+        dx = []
+        if rows2:
+            da, db = torch.empty(rows2, d, device=DEV), torch.empty(rows2, d, device=DEV)
+            lib('c2dsr_ln2_bwd', xs, st, w2, b2, wF, dy2, rows2, d, da, db, keys[0], keys[1], p, base, None, *gr[:4],
+                ws2, s)
+            dx += [da, db]
+        if rows1:
+            d1 = torch.empty(rows1, d, device=DEV)
+            lib('c2dsr_ln_bwd', x1, m1, r1, w1, dy1, rows1, d, d1, 0, None, 0, 0, 0.0, 0, None, gr[4], gr[5], ws1, s)
+            dx.append(d1)
+        return dx
+
+    own = [v.clone() for v in pre]
+    dx_own = backwards(own)
+    both = [v.clone() for v in pre]
+    dx_both = backwards([None] * 6)
+    lib('c2dsr_ln_reduce2', ws2, rows2, ws1, rows1, d, *both, s)
+    torch.cuda.synchronize()
+    for u, v in zip(both + dx_both, own + dx_own):
+        assert torch.equal(u, v)
+    for k in ([0, 1, 2, 3] if rows2 else []) + ([4, 5] if rows1 else []):
+        assert not torch.equal(both[k], pre[k])
+    for k in ([] if rows2 else [0, 1, 2, 3]) + ([] if rows1 else [4, 5]):
+        assert torch.equal(both[k], pre[k])  # no rows: untouched
+
+
+@pytest.mark.parametrize('with_a', [False, True])
+def test_add_dropout(with_a):
+    """c2dsr_add_dropout: y = a + drop(b) (a may be null), the dropout element index offset by idx_base rows."""
+    from c2dsr_amd._lib import lib, stream
+    from oracle.c2dsr_oracle import keep_mask
+    g = torch.Generator().manual_seed(3)
+    rows, d, p, base, keys = 333, 20, 0.3, 1234, (5, 6)
+    a, b = torch.randn(rows, d, generator=g), torch.randn(rows, d, generator=g)
+    y = torch.full((rows, d), float('nan'), device=DEV)
+    lib('c2dsr_add_dropout', a.to(DEV) if with_a else None, b.to(DEV), rows * d, d, keys[0], keys[1], p, base, y,
+        stream())
+    idx = (np.arange(rows)[:, None] + base) * d + np.arange(d)[None, :]
+    keep = torch.from_numpy(keep_mask(idx, keys, p))
+    assert 0.6 < float(keep.double().mean()) < 0.8
+    t = b.double() * keep / (1.0 - float(np.float32(p)))
+    ref = t + a.double() if with_a else t
+    mag = t.abs() + a.double().abs() if with_a else t.abs()
+    assert bool(((y.double().cpu() - ref).abs() <= 4 * 2.0 ** -24 * mag).all())  # one product, one add
+    assert torch.equal(y.cpu()[~keep], a[~keep] if with_a else torch.zeros(int((~keep).sum())))
+    y0 = torch.empty(rows, d, device=DEV)  # p = 0: a + b, a single fp32 add
+    lib('c2dsr_add_dropout', a.to(DEV) if with_a else None, b.to(DEV), rows * d, d, keys[0], keys[1], 0.0, base, y0,
+        stream())
+    assert torch.equal(y0.cpu(), a + b if with_a else b)
+
+
+@pytest.mark.parametrize('p', [0.0, 0.3])
+def test_relu_drop_bwd(p):
+    """c2dsr_relu_drop_bwd: dx = (y > 0)·dy / (1 - p), n no multiple of the block."""
+    from c2dsr_amd._lib import lib, stream
+    g = torch.Generator().manual_seed(4)
+    n = 1001
+    dy, y = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    y[::7] = 0.0
+    dx = torch.full((n,), float('nan'), device=DEV)
+    lib('c2dsr_relu_drop_bwd', dy.to(DEV), y.to(DEV), n, p, dx, stream())
+    ref = torch.where(y > 0, dy.double() / (1.0 - float(np.float32(p))), torch.zeros(n, dtype=torch.float64))
+    assert bool(((dx.double().cpu() - ref).abs() <= 4 * 2.0 ** -24 * ref.abs()).all())
+    assert torch.equal(dx.cpu() == 0, (y <= 0) | (dy == 0))
 
 
 def test_adamw_kernel_vs_oracle():
@@ -955,7 +1075,8 @@ def test_sum_parts(n, nparts):
     assert torch.equal(out.cpu(), out0 + t)
 
 
-@pytest.mark.parametrize('rows,d,p,mapped', [(3001, 256, 0.2, True), (517, 64, 0.0, False), (64, 512, 0.1, False)])
+@pytest.mark.parametrize('rows,d,p,mapped', [(3001, 256, 0.2, True), (517, 64, 0.0, False), (64, 512, 0.1, False),
+                                             (5000, 256, 0.2, True), (300, 768, 0.0, False)])
 def test_add_ln2_equals_two_layernorms(rows, d, p, mapped):
     """c2dsr_add_ln2_fwd / _ln2_bwd (norm2 + the encoder's final norm in one pass) against the two
     c2dsr_add_ln_fwd / c2dsr_ln_bwd calls they replace: outputs, input gradients and all four parameter
